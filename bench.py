@@ -2,7 +2,7 @@
 """Benchmark of the MI355X UVLTrack per-frame forward pass (`forward_test`), reference loop:
 tracking/profile_model.py:30-47 (warm-up, then K timed forwards, sync only at both ends).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--model B|L] [--mode NLBBOX|NL|BBOX]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--model B|L] [--mode NLBBOX|NL|BBOX] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 8 --model L --batch 8          # BASELINE configs[4]: 64 UVLTrack-L sequences, 8 per GPU; a plain
@@ -12,9 +12,17 @@ A step = one pass of the hot path over one batch of synthetic frames per GPU (in
 from the deterministic generator).  Each rank owns its own sequences (independent per-sequence
 shards, weights replicated); the per-shard boxes of every step are all-gathered over RCCL, eight steps per collective, in stream order
 (uvltrack_amd.shard.BoxGatherer: an overlapped collective per step cost the one-sequence frame 11 %, this form a quarter of a percent).
-A timed BLOCK is exactly `--steps` steps between barrier + synchronize on both sides, maximum over ranks; the line reports the
-MEDIAN of `--blocks` such blocks (default: as many as fit in about three seconds, 3..400), so a 20-step run of a 0.7 ms frame is
-not a 15 ms sample.  Rank 0 prints ONE JSON line.
+A timed BLOCK is exactly `--steps` steps between barrier + synchronize on both sides, maximum over ranks; by default one block is
+timed, so `--steps` is the number of timed steps and `ms_per_step` = block time / steps.  `--blocks K` times K such blocks and reports
+their MEDIAN (0: as many as fit in about three seconds, 3..400).  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the steps, writes `--dump-outputs DIR` if asked and prints the line.  `--full` adds what
+takes runs of its own: the profiled frame (`roofline`, `roofline_attention`, `config.launches_per_frame`, `--profile-json`), every
+rank's own step time (`rank_ms_per_step`), the other BASELINE configs (`configs`, `batched`) and the CPU baseline (`cpu_baseline`).
+
+`--dump-outputs DIR` writes the output buffers of the timed path after its last timed step, one DIR/<name>.npy per output (float32;
+the integer `argmax` as float64), at most 64 MB in all: an output too large for its share is stored as a fixed, seeded sample of its
+elements.  Weights and inputs come from fixed seeds, so two builds given the same arguments can be compared output for output.
 
 Launch forms.  Under `torch.distributed.run` (WORLD_SIZE in the environment) every rank joins an RCCL process group -- also when
 there is one rank, so the collective leg runs on a single GPU too.  A plain `python bench.py --gpus N` with N > 1 (or `--dist`)
@@ -43,7 +51,8 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--blocks", type=int, default=0, help="timed blocks of --steps steps (0 = about one second's worth, 3..25)")
+    ap.add_argument("--blocks", type=int, default=1, help="timed blocks of --steps steps, median reported (default 1: --steps is the number of timed "
+                    "steps; 0 = about three seconds' worth, 3..400)")
     ap.add_argument("--batch", type=int, default=1, help="sequences per GPU advanced one frame per step")
     ap.add_argument("--model", default="B", choices=["B", "L"])
     ap.add_argument("--template-size", type=int, default=256)
@@ -55,16 +64,23 @@ def parse_args(argv=None):
     ap.add_argument("--launch", default="eager", choices=["eager", "graph"],
                     help="eager: the frame's kernels are launched each step (one stream for one sequence, two for several; fastest on ROCm 7.2, "
                          "where hipGraphLaunch costs more host time per node than a plain launch); graph: hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batched", action="store_true", help="skip the extra `batched` block (UVLTrack-L z256/x384, 8 sequences: the per-GPU load of BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the profiled frame (rooflines, launch count), per-rank "
+                    "step times, the other BASELINE configs and the CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the timed path's outputs of its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-batched", action="store_true", help="--full without the other BASELINE configs (configs[1], configs[3] and the `batched` block: "
+                    "UVLTrack-L z256/x384, 8 sequences, the per-GPU load of BASELINE configs[4])")
     ap.add_argument("--cpu-frames", type=int, default=8)
     ap.add_argument("--cpu-threads", type=int, default=32)
-    ap.add_argument("--profile-json", default=None, help="also write the per-kernel breakdown to this file")
+    ap.add_argument("--profile-json", default=None, help="also write the per-kernel breakdown to this file (implies --full: it comes from the profiled frame)")
     ap.add_argument("--dist", action="store_true", help="run under torch.distributed.run even with --gpus 1 (RCCL process group of one rank)")
     ap.add_argument("--gather-every", type=int, default=0, help="steps per box all-gather (0 = from the step time: 1 when a step is >= 2 ms, else 8; uvltrack_amd/shard.py)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="tools only: uvl_tune_set(KEY, VALUE) on the engine's handle (include/uvltrack_hip.h: uvl_tuning); recorded in the line")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.profile_json:
+        args.full = True
+    return args
 
 
 def build_spec(model, template_size, search_size):
@@ -182,6 +198,38 @@ def throughput(world: int, per_rank_units: int, steps: int, block_seconds) -> fl
     return world * per_rank_units * steps / float(np.median(block_seconds))
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6          # --dump-outputs: array data of all files together
+ECHOED_INPUTS = ("flag", "prompt", "prompts")      # entries of the output dict that hand the caller's own inputs back
+
+
+def dump_outputs(outs, out_dir, budget: int = DUMP_BUDGET_BYTES, seed: int = 0):
+    """--dump-outputs: every array the step computed into `outs` (HipEngine.alloc_outputs / capture), one out_dir/<name>.npy each, float32
+    (integer outputs as float64, exact).  Smallest first, each output gets an equal share of what the budget has left; one larger than its
+    share is stored as a seeded sample of that many elements (flattened, indices sorted: the same shape always gives the same indices).
+    Returns {name: (shape, stored elements)}."""
+    import zlib
+    host = {}
+    for k, v in outs.items():
+        if k in ECHOED_INPUTS:
+            continue
+        a = v.detach().cpu().numpy()
+        host[k] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = budget, {}
+    names = sorted(host, key=lambda k: (host[k].nbytes, k))
+    for n, k in enumerate(names):
+        a = host[k]
+        share = left // (len(names) - n)
+        if a.nbytes > share:
+            rng = np.random.default_rng([seed, zlib.crc32(k.encode())])
+            idx = np.sort(rng.choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        left -= a.nbytes
+        written[k] = (tuple(host[k].shape), int(a.size))
+    return written
+
+
 def rank_step_times(env, step_fn, sync, n: int = 10):
     """Per-rank step time (ms): every rank runs `n` steps on its own -- no collective in them, so a rank cannot hide behind the others' wait -- and the figures are
     gathered with ONE all_gather outside the timed blocks.  A straggler GPU shows up in the one line (min / median / max, the slowest rank's index, the spread);
@@ -268,8 +316,11 @@ def pick_gather_every(step_fn, sync, env, forced: int = 0) -> int:
     return choose_every(env.max_over_ranks((time.perf_counter() - t0) / 5) * 1e3)
 
 
-def measure(torch, dev, env, rank, spec, B, flag_val, args, skip_text, reuse_text, use_graph, steps, warmup, blocks, seed, eng=None, max_batch=None):
-    """Build an engine for `spec` (or take `eng`, built for the same spec), run the timed blocks; returns (times, engine, targs, outs)."""
+def measure(torch, dev, env, rank, spec, B, flag_val, args, skip_text, reuse_text, use_graph, steps, warmup, blocks, seed, eng=None, max_batch=None,
+            rank_times=True, on_timed=None):
+    """Build an engine for `spec` (or take `eng`, built for the same spec), run the timed blocks; returns (times, engine, targs, outs).
+    on_timed(outs), if given, is called right after the timed blocks, before any further step; rank_times: also time every rank's own
+    steps (eng.rank_ms, else None)."""
     from uvltrack_amd import weightgen as wg
     from uvltrack_amd.engine import HipEngine
     from uvltrack_amd.shard import BoxGatherer
@@ -292,6 +343,10 @@ def measure(torch, dev, env, rank, spec, B, flag_val, args, skip_text, reuse_tex
     else:
         _, outs = eng.capture(*targs, skip_text=skip_text)
         step_fn = eng.replay
+    if on_timed is not None:
+        for k, v in outs.items():                     # a buffer the frame leaves alone (text rows when the branch is skipped) dumps as zeros
+            if k not in ECHOED_INPUTS:                # (those are the step's own input tensors)
+                v.zero_()
     # RCCL all-gather of the per-shard boxes: rank r owns sequences [r*B, (r+1)*B).  One collective per step wherever a
     # step is >= 2 ms (configs[4]); sub-millisecond frames send eight steps per collective (shard.choose_every): the cadence comes from a
     # few untimed steps, the slowest rank's figure, so that every rank builds the same groups
@@ -304,8 +359,10 @@ def measure(torch, dev, env, rank, spec, B, flag_val, args, skip_text, reuse_tex
     finite = bool(torch.isfinite(outs["bbox_map"]).all().item()) and bool(torch.isfinite(outs["logits"]).all().item())
     if not finite:
         raise SystemExit("bench.py: the forward pass produced non-finite outputs -- timing of a broken path is not reported")
+    if on_timed is not None:
+        on_timed(outs)
     eng.gather_every = gatherer.every if gatherer is not None else None
-    eng.rank_ms = rank_step_times(env, step_fn, torch.cuda.synchronize)          # (a collective: every rank, outside the timed blocks)
+    eng.rank_ms = rank_step_times(env, step_fn, torch.cuda.synchronize) if rank_times else None     # (a collective: every rank, outside the timed blocks)
     return times, eng, targs, outs
 
 
@@ -430,8 +487,11 @@ def main():
     reuse_text = bool(args.reuse_text and not skip_text)
     use_graph = args.launch == "graph"
 
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = lambda outs_: dump_outputs(outs_, args.dump_outputs)
     times, eng, targs, outs = measure(torch, dev, env, rank, spec, B, flag_val, args, skip_text, reuse_text, use_graph,
-                                      args.steps, args.warmup, args.blocks, seed=1000)
+                                      args.steps, args.warmup, args.blocks, seed=1000, rank_times=args.full, on_timed=dump)
     elapsed = float(np.median(times))
     rank_ms = eng.rank_ms
 
@@ -439,7 +499,6 @@ def main():
         fps = throughput(world, B, args.steps, times)
         frame_ms = elapsed / args.steps * 1e3
         single_stream = (B == 1 or skip_text or reuse_text) and not use_graph
-        roofline, roofline_attention, by_kernel, prof, n_launch = kernel_rooflines(eng, targs, spec, B, frame_ms, skip_text, reuse_text, single_stream, args.model)
         flops_frame = spec.flops_per_frame(skip_text=skip_text, reuse_text=reuse_text)
         from uvltrack_amd.spec import state_dict_schema
         weight_bytes = 2.0 * sum(int(np.prod(s)) for n, s in state_dict_schema(spec, False).items()
@@ -451,12 +510,10 @@ def main():
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "blocks": len(times), "block_ms": [round(x * 1e3, 3) for x in times], "statistic": "median of the blocks (each: exactly `steps` steps, max over ranks)",
-            # every rank's own ms per step (ten steps without a collective, gathered outside the timed region): `value` follows the SLOWEST rank
-            "rank_ms_per_step": rank_ms,
             "config": {"workload": "UVLTrack-%s z%d/x%d/T%d %s%s, %d sequence(s)/GPU, batch shards + RCCL all-gather of boxes" % (
                 args.model, spec.template_size, spec.search_size, spec.text_len, args.mode, " (text branch skipped)" if skip_text else (" (text branch reused from the first frame)" if reuse_text else ""), B),
                 "per_gpu_batch": B, "global_batch": B * world, "tokens_visual": spec.nv, "tokens_joint": spec.nj,
-                "gflop_per_frame": flops_frame / 1e9, "launches_per_frame": n_launch,
+                "gflop_per_frame": flops_frame / 1e9,
                 "launch": "hipgraph" if use_graph else ("eager-1-stream" if single_stream else "eager-2-streams"), "parallelism": "dp%d" % world,
                 # the box all-gather's cadence (uvltrack_amd/shard.py): steps per collective and the worst-case lateness of a step's boxes,
                 # in steps; null without a process group (one plain process: nothing to gather)
@@ -465,12 +522,19 @@ def main():
             "frame_mfma_frac": flops_frame * fps / 1e12 / (PEAK_BF16_TFLOPS * world),
             "frame_hbm_frac": (weight_bytes * (args.steps / elapsed)) / 1e9 / PEAK_HBM_GBS,
             "outputs_finite": True,
-            "roofline": roofline,
         }
         if args.tune:
             line["config"]["tune"] = list(args.tune)              # NOT the default path: heuristics overridden for an A/B
-        if roofline_attention is not None:
-            line["roofline_attention"] = roofline_attention
+        if args.dump_outputs:
+            line["dump_outputs"] = os.path.abspath(args.dump_outputs)
+        if args.full:
+            roofline, roofline_attention, by_kernel, prof, n_launch = kernel_rooflines(eng, targs, spec, B, frame_ms, skip_text, reuse_text, single_stream, args.model)
+            line["config"]["launches_per_frame"] = n_launch
+            # every rank's own ms per step (ten steps without a collective, gathered outside the timed region): `value` follows the SLOWEST rank
+            line["rank_ms_per_step"] = rank_ms
+            line["roofline"] = roofline
+            if roofline_attention is not None:
+                line["roofline_attention"] = roofline_attention
     eng.close()
     del eng, targs, outs
 
@@ -494,7 +558,7 @@ def main():
                "frame_hbm_frac": xwb * (xfps / Bx) / 1e9 / PEAK_HBM_GBS, "launches_per_frame": xn, "roofline": xroof, "roofline_attention": xattn}
         return blk, xeng
 
-    if world == 1 and not args.no_batched and not (args.model == "L" and B == 8):
+    if args.full and world == 1 and not args.no_batched and not (args.model == "L" and B == 8):
         c1, e1 = extra("B", "BBOX", True, 1, None, "UVLTrack-B z256/x256 BBOX, text branch skipped, 1 sequence (BASELINE configs[1])", 3000)
         e1.close()
         c3, eL = extra("L", "NLBBOX", False, 1, None, "UVLTrack-L z256/x384/T40 NLBBOX, 1 sequence (BASELINE configs[3])", 4000)
@@ -503,7 +567,7 @@ def main():
         eL.close()
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(spec, args, [flag_val] * B)
         if args.profile_json:
             with open(args.profile_json, "w") as f:

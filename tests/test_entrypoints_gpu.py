@@ -74,7 +74,7 @@ def test_bench_self_launch_one_rank_rccl():
     under torch.distributed.run, joins an RCCL ("nccl") process group of ONE rank and all-gathers the boxes every step -- the same code
     as N ranks.  (No N > 1 run has been possible: one GPU per box.)"""
     out = _run([sys.executable, "bench.py", "--gpus", "1", "--dist", "--model", "L", "--batch", "8", "--steps", "3", "--warmup", "2", "--blocks", "1",
-                "--no-cpu-baseline"])
+                "--full", "--no-cpu-baseline"])
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1
     assert line["config"]["global_batch"] == 8 and line["config"]["parallelism"] == "dp1"
@@ -83,7 +83,7 @@ def test_bench_self_launch_one_rank_rccl():
 
 
 def test_bench_default_line_has_the_contract_fields():
-    out = _run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--blocks", "3", "--no-batched", "--cpu-frames", "1"])
+    out = _run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "5", "--blocks", "3", "--no-batched", "--cpu-frames", "1"])
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline"):
@@ -93,3 +93,32 @@ def test_bench_default_line_has_the_contract_fields():
     assert r["bound"] in ("mfma", "hbm") and r["regime"] in ("mfma", "hbm", "latency") and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert (r["traffic"] is None) == (r["traffic_source"] is None)
     assert line["cpu_baseline"]["kind"] == "port-torch" and line["cpu_baseline"]["cores"] >= 1 and line["cpu_baseline"]["numpy_port"]["value"] > 0
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full): ONE block of exactly --steps timed steps, the headline fields and nothing that takes runs of its own; --dump-outputs
+    leaves the last step's outputs, which match the numpy oracle on the same seeded weights and inputs at smoke()'s gates."""
+    import numpy as np
+    from oracle import uvl_oracle as O
+    from uvltrack_amd import weightgen as wg
+    from uvltrack_amd.spec import spec_b
+    out = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path)])
+    line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 20 and line["blocks"] == 1 and line["outputs_finite"] and line["unit"] == "frames/s" and line["dtype"] == "bf16"
+    assert abs(line["ms_per_step"] * 20 - line["block_ms"][0]) < 1e-2 and abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    for k in ("roofline", "roofline_attention", "rank_ms_per_step", "configs", "batched", "cpu_baseline"):
+        assert k not in line, k
+    files = sorted(os.listdir(tmp_path))
+    assert "bbox_map.npy" in files and "cls_score_test.npy" in files and "prompt.npy" not in files
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 * 10 ** 6 + 128 * len(files)
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    spec = spec_b(256, 256)                                          # the default workload: UVLTrack-B z256/x256, NLBBOX, weights seed 0, inputs seed 1000
+    inp = wg.make_inputs(spec, batch=1, seed=1000, flags=[2])
+    ref = O.forward_test(wg.make_state_dict(spec, 0, include_unused=False), spec, inp["template"], inp["search"], inp["ids"], inp["mask"], inp["prompt"], inp["flag"])
+    for k, tol in (("bbox_map", 1e-2), ("cls_score_test", 1e-2), ("cont_score", 5e-2), ("logits", 0.15)):
+        assert got[k].shape == ref[k].shape, k
+        err = float(np.abs(got[k] - ref[k]).max())
+        assert err <= tol, "%s: %g > %g" % (k, err, tol)

@@ -12,7 +12,7 @@ import bench  # noqa: E402
 
 
 def run(k1, k4, extra=()):
-    sys.argv = ["bench.py", "--no-cpu-baseline", "--no-batched", "--steps", "300", "--warmup", "50", "--blocks", "5",
+    sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-batched", "--steps", "300", "--warmup", "50", "--blocks", "5",
                 "--tune", "sk_k1=%d" % k1, "--tune", "sk_k4=%d" % k4, *extra]
     buf = io.StringIO()
     with redirect_stdout(buf):

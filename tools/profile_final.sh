@@ -12,5 +12,6 @@ python tools/attn_bench.py --cfgs 8,10,11 > gpurun_out/${TAG}_attn_bench.txt 2>&
 python tools/lib_compare.py 8 32 > gpurun_out/${TAG}_lib_compare.txt 2>&1
 python bench.py --batch 32 --steps 30 --warmup 5 --no-cpu-baseline --no-batched > gpurun_out/${TAG}_bench_b32.json 2>/dev/null
 python bench.py --batch 8 --steps 60 --warmup 10 --no-cpu-baseline --no-batched > gpurun_out/${TAG}_bench_b8.json 2>/dev/null
-python bench.py > gpurun_out/${TAG}_bench_full.json 2>/dev/null
+RESULTS=${RESULTS:-bench_results}; mkdir -p "$RESULTS"          # folder of the --full bench line
+python bench.py --full > "$RESULTS/${TAG}_bench_full.json" 2>/dev/null
 tail -3 gpurun_out/$TAG.log; tail -3 gpurun_out/${TAG}_attn.log; cut -c1-200 gpurun_out/${TAG}_bench_b32.json

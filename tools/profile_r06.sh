@@ -19,5 +19,6 @@ find gpurun_out/${TAG}_old -name "*kernel_trace.csv" -delete; find gpurun_out/${
 STEPS=30 WARMUP=5 timeout 1200 bash tools/profile_bench.sh gpurun_out/${TAG}_L8 --model L --batch 8 --template-size 256 --search-size 384 > gpurun_out/${TAG}_L8.log 2>&1
 timeout 300 python bench.py --batch 8 --steps 60 --warmup 10 --no-cpu-baseline --no-batched > gpurun_out/${TAG}_bench_b8.json 2>/dev/null
 timeout 300 python bench.py --batch 32 --steps 30 --warmup 5 --no-cpu-baseline --no-batched > gpurun_out/${TAG}_bench_b32.json 2>/dev/null
-timeout 600 python bench.py > gpurun_out/${TAG}_bench_full.json 2>/dev/null
+RESULTS=${RESULTS:-bench_results}; mkdir -p "$RESULTS"          # folder of the --full bench line
+timeout 600 python bench.py --full > "$RESULTS/${TAG}_bench_full.json" 2>/dev/null
 tail -3 gpurun_out/$TAG.log; cat gpurun_out/${TAG}_ab_fold.txt | tail -6
